@@ -1,6 +1,6 @@
 """Headline benchmark: scaled GEMM fp8(e4m3fn) x fp8 -> bf16, M=4096 K=4096 N=11008 (BASELINE.json C3).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5|c1|c4readme|c4decode|midm]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5|c1|c4readme|c4decode|midm] [--dump-outputs DIR]
 
 One "step" = one `scaled_gemm` call (public op: output allocation + fused GEMM/scale/cast kernel) on
 synthetic inputs that are already resident in HBM, built with the reference benchmark's recipe
@@ -42,6 +42,11 @@ FLOPs / time of (GEMM + gather + unpack to row-major).  GEMM-only throughput, th
 weak-scaling data-parallel C3 run (every rank its own 4096-token batch, replicated weights, no collective) are side fields.
 The N = 1 line (C3, the BASELINE metric) always carries `c5_one_gpu`, the one-GPU figure of that same C5 problem, so that
 strong-scaling efficiency follows from the lines alone: line(N).value / line(1).c5_one_gpu.value / N.
+
+`--dump-outputs DIR` (rank 0): after the timed region of the headline, what its LAST timed call returned -- the arrays a caller
+of the op receives -- goes to DIR/<name>.npy in float32 (exact for every output dtype here).  An output larger than the budget
+(DUMP_MAX_BYTES in all) is written as a fixed, seeded sample of its rows; the line's `dump_outputs` field names the files, the
+full shapes and the rows kept.  The inputs are seeded, so two builds run with the same arguments can be compared file by file.
 """
 
 from __future__ import annotations
@@ -89,6 +94,8 @@ WORKLOADS = {
 CLOCK_RAMP_S = 0.15  # the GPU needs ~20 ms of load to leave its idle clocks: the ramp of the `burst` side figure
 SUSTAINED_S = 2.0  # continuous load in front of the timed region and behind `roofline.frac`
 SIDE_SUSTAINED_S = 0.8  # the same for the side legs (c1, c2, c4, c4readme)
+DUMP_MAX_BYTES = 60 << 20  # --dump-outputs: array bytes of all .npy files together (with their headers, under 64 MB)
+DUMP_SAMPLE_SEED = 0  # the rows an over-budget output is sampled at: the same in every run and every build
 
 
 def dist_env() -> tuple[int, int, int]:
@@ -328,9 +335,11 @@ def barrier_sync(world: int, device: torch.device | None = None) -> None:
     device_sync(device)
 
 
-def timed_region(fn, steps: int, warmup: int, world: int, device: torch.device, ramp_s: float = CLOCK_RAMP_S, load=None) -> float:
+def timed_region(fn, steps: int, warmup: int, world: int, device: torch.device, ramp_s: float = CLOCK_RAMP_S, load=None,
+                 keep: list | None = None) -> float:
     """Load phase (`load()` if given -- seconds of the kernel's own launches -- else `ramp_s` of calls), W warm-up calls, then
-    exactly `steps` calls between barrier+synchronize; max over ranks (s)."""
+    exactly `steps` calls between barrier+synchronize; max over ranks (s).  `keep`: the last timed call's return value is
+    appended to it."""
     if load is not None:
         load()
     else:
@@ -356,10 +365,14 @@ def timed_region(fn, steps: int, warmup: int, world: int, device: torch.device, 
         fn()
     barrier_sync(world, device)
     t0 = time.perf_counter()
-    for _ in range(steps):
+    # every result but the last is dropped before the next call starts: each call gets the block its predecessor freed
+    for _ in range(steps - 1):
         fn()
+    last = fn() if steps > 0 else None
     barrier_sync(world, device)
     elapsed = time.perf_counter() - t0
+    if keep is not None:
+        keep.append(last)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -368,7 +381,7 @@ def timed_region(fn, steps: int, warmup: int, world: int, device: torch.device, 
 
 
 def nshard_c5(world: int, rank: int, device: torch.device, steps: int, warmup: int, shape: tuple[int, int, int] | None = None,
-              direct: bool = False) -> dict:
+              direct: bool = False, keep: list | None = None) -> dict:
     """C5: M=8192 K=8192 N=28672 with N sharded over the ranks, C all-gathered over xGMI (RCCL).
 
     Timed: (1) the local GEMM only, (2) GEMM + all-gather in the block-major layout the collective produces, (3) GEMM +
@@ -402,7 +415,7 @@ def nshard_c5(world: int, rank: int, device: torch.device, steps: int, warmup: i
         mismatches += int((want.view(torch.int16) != got.view(torch.int16)).sum().item())
     t_gemm = timed_region(lambda: op.local_gemm(a, bt_loc.T, sa, sb_loc), steps, warmup, world, device)
     t_blocks = timed_region(lambda: op.gathered_panels(a, bt_loc.T, sa, sb_loc), steps, warmup, world, device)
-    t_full = timed_region(lambda: op(a, bt_loc.T, sa, sb_loc), steps, warmup, world, device)
+    t_full = timed_region(lambda: op(a, bt_loc.T, sa, sb_loc), steps, warmup, world, device, keep=keep)
     flops = 2.0 * m * n * k
     direct_fields = {}
     if direct and world > 1:
@@ -678,12 +691,44 @@ def measured_peak(leg: Leg, seconds: float) -> dict | None:
         return {"error": repr(exc)}
 
 
+def dump_outputs(returned, directory: Path, names: tuple[str, ...] = ("output", "scale"), max_bytes: int = DUMP_MAX_BYTES) -> dict:
+    """--dump-outputs: what the op returned (a tensor, or a tuple of them: scaled_int8_quant's (output, scale)), each array to
+    `directory`/<name>.npy in float32 (float64 stays float64).  When all of them together would exceed `max_bytes`, each is cut to
+    the share of the budget its size earns: a sorted sample of its rows, drawn by a generator seeded with DUMP_SAMPLE_SEED.
+    Returns the `dump_outputs` field of the line."""
+    import numpy as np
+
+    returned = returned if isinstance(returned, tuple) else (returned,)
+    assert len(returned) <= len(names), f"{len(returned)} arrays returned, names for {len(names)}"
+    arrays = dict(zip(names, returned))
+    directory.mkdir(parents=True, exist_ok=True)
+    wide = {name: torch.float64 if t.dtype == torch.float64 else torch.float32 for name, t in arrays.items()}
+    total = sum(t.numel() * wide[name].itemsize for name, t in arrays.items())
+    files = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        rec = {"shape": list(t.shape), "dtype": str(t.dtype).removeprefix("torch.")}
+        if total > max_bytes and t.dim() >= 1 and t.shape[0] > 1:
+            row_bytes = t[0].numel() * wide[name].itemsize
+            rows = max(1, min(t.shape[0], int(max_bytes * (t.numel() * wide[name].itemsize / total)) // row_bytes))
+            g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+            idx = torch.randperm(t.shape[0], generator=g)[:rows].sort().values
+            t = t[idx.to(t.device)]
+            rec["rows_kept"] = rows
+            rec["rows_sample"] = f"torch.randperm({rec['shape'][0]}, generator seeded {DUMP_SAMPLE_SEED})[:{rows}], sorted"
+        np.save(directory / f"{name}.npy", t.to(wide[name]).cpu().numpy())
+        rec["file"] = f"{name}.npy"
+        files[name] = rec
+    return {"dir": str(directory), "arrays": files}
+
+
 def measure_leg(leg: Leg, steps: int, warmup: int, world: int, sustained_s: float, with_burst: bool, with_cold: bool, with_probe: bool,
-                with_peak: bool, with_cpu: bool, with_parity: bool = True) -> dict:
+                with_peak: bool, with_cpu: bool, with_parity: bool = True, keep: list | None = None) -> dict:
     """One workload, measured: op-level timed region after `sustained_s` of the kernel's own load, kernel-level roofline
     (sustained / burst / cold), the measured ceiling and the CPU oracle's rate.  `with_parity`: BEFORE anything is timed an output
     of the op that will be timed is checked against the CPU oracle (Leg.parity), and AFTER the timed region the buffer the
-    kernel-event timer wrote under sustained load (`leg.out`: the launches behind `roofline`) is checked the same way."""
+    kernel-event timer wrote under sustained load (`leg.out`: the launches behind `roofline`) is checked the same way.  `keep`
+    receives the return value of the last call of the timed region behind `value`."""
     device = leg.device
     burst = None
     parity = None
@@ -701,9 +746,9 @@ def measure_leg(leg: Leg, steps: int, warmup: int, world: int, sustained_s: floa
         sus["ms"], sus["s"] = sustained_kernel_ms(leg.timer, sustained_s)
 
     if sustained_s > 0:
-        elapsed = timed_region(leg.step, steps, warmup, world, device, load=load)
+        elapsed = timed_region(leg.step, steps, warmup, world, device, load=load, keep=keep)
     else:
-        elapsed = timed_region(leg.step, steps, warmup, world, device)
+        elapsed = timed_region(leg.step, steps, warmup, world, device, keep=keep)
         sus["ms"], sus["s"] = leg.timer(max(20, min(steps, 200))), 0.0
     k_ms = sus["ms"]
     roofline = {"bound": "hbm" if leg.hbm_bound else "mfma", "achieved": round(leg.rate(k_ms), 2), "peak": leg.roof_peak, "unit": leg.unit,
@@ -1000,7 +1045,12 @@ def main() -> None:
                     help="bare --gpus N > 1 only: ranks still alive after S seconds dump their stacks and are killed; exit code 124 (0 = wait for ever)")
     ap.add_argument("--all-ranks-on-device0", action="store_true",
                     help="dry-run aid: put every rank on cuda:0 (needs --backend gloo)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed call of the headline returned to DIR/<name>.npy (float32; a seeded row "
+                         f"sample when over {DUMP_MAX_BYTES >> 20} MiB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1") or 1) == 1:
         # called bare, as the driver calls N = 1 (no launcher's environment, or a stale one-rank one inherited from the caller):
         # be the launcher (before anything touches the GPU)
@@ -1034,8 +1084,12 @@ def main() -> None:
     if args.workload == "c5" or (world > 1 and args.workload == "c3" and not args.dp):
         # multi-GPU headline (and `--workload c5` on one GPU): BASELINE config C5, strong scaling over N
         shape = tuple(int(v) for v in args.c5_shape.split(",")) if args.c5_shape else None
-        res = nshard_c5(world, rank, device, args.steps, args.warmup, shape=shape, direct=args.c5_direct)
+        keep = [] if args.dump_outputs else None
+        res = nshard_c5(world, rank, device, args.steps, args.warmup, shape=shape, direct=args.c5_direct, keep=keep)
         extra = {}
+        if keep and rank == 0:  # the gathered row-major C: the same on every rank
+            extra["dump_outputs"] = dump_outputs(keep[0], Path(args.dump_outputs))
+        keep = None
         if world > 1 and args.workload == "c3":
             try:  # side field: weak-scaling data parallel C3 (no collective on the data path)
                 a, b, sa, sb = make_scaled("scaled_fp8", m, k, n, device, seed=rank)
@@ -1051,10 +1105,15 @@ def main() -> None:
     full = not args.quick
     leg = Leg(args.workload, device, seed=rank)
     sustained_s = (SUSTAINED_S if world == 1 else 0.0) if full else 0.0
+    keep = [] if args.dump_outputs else None
     res = measure_leg(leg, args.steps, args.warmup, world, sustained_s, with_burst=full and world == 1,
                       with_cold=full and not args.no_cold and leg.kind != "quant_int8", with_probe=world == 1 and full and not args.no_probe,
                       with_peak=world == 1 and full and not args.no_peak, with_cpu=world == 1 and rank == 0 and not args.no_cpu_baseline,
-                      with_parity=not args.no_parity)
+                      with_parity=not args.no_parity, keep=keep)
+    dumped = None
+    if keep and rank == 0:
+        dumped = dump_outputs(keep[0], Path(args.dump_outputs))
+    keep = None
     if args.workload == "c3":
         metric = "effective TFLOP/s + % MFMA roofline, scaled-GEMM fp8xbf16 4096x4096x11008"
     elif leg.kind == "quant_int8":
@@ -1073,6 +1132,8 @@ def main() -> None:
         },
         "roofline": res["roofline"],
     }
+    if dumped is not None:
+        result["dump_outputs"] = dumped
     if "parity" in res:
         result["parity"] = res["parity"]
     if "burst" in res:

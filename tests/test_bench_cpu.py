@@ -134,3 +134,41 @@ def test_committed_traffic_table_matches_the_kernel_sources():
     for name in ("c1", "c2", "c3", "c4", "c4readme"):
         value, why = bench.load_traffic(name)
         assert value == table[name]["hbm_bytes_per_launch"], (name, why)
+
+
+def test_timed_region_makes_exactly_steps_calls_and_keeps_the_last_result():
+    """--steps is the number of timed calls, and what --dump-outputs writes is the return value of the last of them."""
+    calls = []
+
+    def step():
+        calls.append(len(calls))
+        return torch.tensor([float(len(calls))])
+
+    keep = []
+    bench.timed_region(step, 7, 3, 1, CPU, load=lambda: None, keep=keep)
+    assert len(calls) == 3 + 7 and len(keep) == 1 and keep[0].item() == 10.0
+
+
+def test_dump_outputs_writes_float32_within_the_budget_and_samples_the_same_rows_every_time(tmp_path):
+    import numpy as np
+
+    g = torch.Generator().manual_seed(0)
+    q = torch.randint(-128, 128, (300, 50), dtype=torch.int8, generator=g)
+    c = torch.randn(300, 50, generator=g).to(torch.bfloat16)
+    scale = torch.tensor([2.1])
+
+    rec = bench.dump_outputs((q, scale), tmp_path / "all")  # under the budget: every element, exactly
+    assert set(rec["arrays"]) == {"output", "scale"} and "rows_kept" not in rec["arrays"]["output"]
+    got = np.load(tmp_path / "all" / "output.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, q.float().numpy())
+    assert np.array_equal(np.load(tmp_path / "all" / "scale.npy"), scale.numpy())
+
+    budget = 80 * 50 * 4
+    first = bench.dump_outputs(c, tmp_path / "a", max_bytes=budget)["arrays"]["output"]
+    again = bench.dump_outputs(c.clone(), tmp_path / "b", max_bytes=budget)["arrays"]["output"]
+    a, b = np.load(tmp_path / "a" / "output.npy"), np.load(tmp_path / "b" / "output.npy")
+    assert first == again and first["shape"] == [300, 50] and first["rows_kept"] == 80
+    assert a.dtype == np.float32 and a.shape == (80, 50) and a.nbytes <= budget and np.array_equal(a, b)
+    # the sample is a sorted subset of the full output's rows, converted exactly
+    rows = {tuple(r) for r in c.float().numpy()}
+    assert all(tuple(r) in rows for r in a) and len({tuple(r) for r in a}) == 80
