@@ -22,7 +22,9 @@ DT_FP32, DT_FP16, DT_BF16, DT_FP8_E4M3FN, DT_INT8, DT_UINT8, DT_INT32, DT_UINT32
 ZP_NONE, ZP_SCALAR, ZP_TENSOR = range(3)
 (TUNE_GEMM_VARIANT, TUNE_MIXED_TILE_NT, TUNE_SKINNY_NO_SPLITK, TUNE_SKINNY_MODE, TUNE_TILE_SCHEDULE, TUNE_PERSISTENT, TUNE_EPILOGUE, TUNE_DIAG,
  TUNE_MID_STAGES, TUNE_MIXED_SPLITK, TUNE_SKINNY_GATHER, TUNE_MIXED_KERNEL, TUNE_MID_SPLITK, TUNE_SKINNY_CHUNKS, TUNE_MIXED_STRIP_ROWS,
- TUNE_COUNT) = range(16)
+ TUNE_BLOCKWISE_KERNEL, TUNE_COUNT) = range(17)
+# TUNE_BLOCKWISE_KERNEL values (conch_debug_blockwise_plan reports the same numbers)
+BLOCKWISE_AUTO, BLOCKWISE_TILES, BLOCKWISE_SPLITK, BLOCKWISE_DECODE = range(4)
 (VARIANT_AUTO, VARIANT_GENERIC, VARIANT_MFMA_SIMPLE, VARIANT_MFMA_PINGPONG, VARIANT_MFMA_SKINNY,
  VARIANT_MFMA_PINGPONG2, VARIANT_MFMA_MID, VARIANT_MFMA_ASM1W) = range(8)
 
@@ -132,6 +134,9 @@ _SIGNATURES = {
         c_int,
         [c_void_p] * 5 + [_I64] * 8 + [c_int] * 6 + [c_void_p],
     ),
+    "conch_scaled_gemm_blockwise": (c_int, [c_void_p] * 6 + [_I64] * 10 + [c_int, c_void_p]),
+    "conch_scaled_gemm_blockwise_workspace_bytes": (_I64, [_I64, _I64, _I64]),
+    "conch_debug_blockwise_plan": (c_int, [_I64, _I64, _I64, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "conch_time_mixed_precision_gemm": (
         c_int,
         [c_void_p] * 5 + [_I64] * 8 + [c_int] * 6 + [c_void_p, c_int, ctypes.POINTER(c_float)],

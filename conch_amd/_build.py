@@ -13,7 +13,7 @@ PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libconch_amd.so"
-SOURCES = ["capi.hip", "gemm_asm.hip", "quant.hip", "quant_dynamic.hip", "gemm_generic.hip", "repack.hip", "gemm_mfma.hip", "gemm_mid.hip", "gemm_skinny.hip", "gemm_mixed.hip", "gemm_mixed_strip.hip", "gemm_mixed_skinny.hip", "gemm_modes.hip", "bnb.hip"]
+SOURCES = ["capi.hip", "gemm_asm.hip", "quant.hip", "quant_dynamic.hip", "gemm_generic.hip", "repack.hip", "gemm_mfma.hip", "gemm_mid.hip", "gemm_skinny.hip", "gemm_mixed.hip", "gemm_mixed_strip.hip", "gemm_mixed_skinny.hip", "gemm_modes.hip", "bnb.hip", "gemm_blockscale.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
     "--offload-arch=gfx950",
@@ -25,6 +25,9 @@ FLAGS = [
     f"-I{ROOT / 'include'}",
     f"-I{CSRC}",
 ]
+# per-source additions: the block-scaled GEMM's K loop must keep its scale FMAs scalar (v_fmac_f32), which the SLP vectoriser
+# otherwise pairs into v_pk_fma_f32 (gemm_blockscale.hip, scale_add)
+SOURCE_FLAGS = {"gemm_blockscale.hip": ["-fno-slp-vectorize"]}
 
 
 # every hipcc process of this interpreter -- the product build, the diagnostic twin and experiment variants may run at the same
@@ -115,7 +118,7 @@ def build(force: bool = False, verbose: bool = False, probe: bool = False, varia
         o = objdir / (s.stem + ".o")
         deps = [s, *headers, *(asm_incs if src == "gemm_asm.hip" else [])]
         if force or _stale(o, deps):
-            cmd = [HIPCC, *flags, f"-I{objdir}", "-c", str(s), "-o", str(o)]
+            cmd = [HIPCC, *flags, *SOURCE_FLAGS.get(src, ()), f"-I{objdir}", "-c", str(s), "-o", str(o)]
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)
             with _COMPILE_SLOTS:

@@ -180,7 +180,9 @@ typedef enum conch_tuning_key {
                                   leaves its partial sums (fewer slabs for a long K): 0 = auto, n >= 1 = that many */,
   CONCH_TUNE_MIXED_STRIP_ROWS = 14 /* column-strip mixed_precision_gemm (gemm_mixed_strip.hip): rows of its tile: 0 = auto (64 / 128
                                       rows for M <= 64 / 128 in the K-split forms, else 256), 64 / 128 / 256 = force */,
-  CONCH_TUNE__COUNT = 15 /* number of keys (array bound; not a key) */
+  CONCH_TUNE_BLOCKWISE_KERNEL = 15 /* block-scaled fp8 GEMM (conch_scaled_gemm_blockwise): 0 = auto, 1 = 128x128 tiles, 2 = tiles with
+                                      split-K, 3 = the decode kernel (any M: 64-row blocks) */,
+  CONCH_TUNE__COUNT = 16 /* number of keys (array bound; not a key) */
 } conch_tuning_key_t;
 
 int conch_abi_version(void);
@@ -457,6 +459,27 @@ int conch_time_mixed_precision_gemm(void* c, const void* x, const int32_t* w_q_p
                                     int weight_bits, int weight_bias, int group_size, int zp_mode,
                                     int x_dtype, int out_dtype, void* stream, int iters,
                                     float* avg_ms);
+
+/*
+ * Block-scaled fp8 GEMM (DeepSeek-V3 / "1x128 activations, 128x128 weights"), e4m3fn operands only:
+ *   C[m][n] = out_dtype( sum_kb (scale_a[m][kb] * scale_b[n / 128][kb]) * sum_{k in block kb} a[m][k] * b[k][n] )  (+ bias[n], in out_dtype)
+ * kb = k / 128.  K % 128 == 0.  A: [M][K] rows lda bytes apart; B^T: [N][K] rows ldb bytes apart (the NT contract, b = w.T);
+ * lda, ldb multiples of 16.  C: [M][N] of out_dtype (FP16 / BF16), rows ldc elements apart, unit column stride.
+ * scale_a: fp32 [M][K/128] at scale_a + m * sa_stride_m + kb * sa_stride_kb; scale_b: fp32 [ceil(N/128)][K/128] at
+ * scale_b + nb * sb_stride_nb + kb * sb_stride_kb (strides in elements, any layout).  bias: NULL or [N] of out_dtype.
+ * Every scale block's partial product is scaled in fp32 before it is added: the scales cannot ride in the epilogue.  Results are
+ * deterministic (fixed-order reductions, no atomics).  Split-K forms use the library scratch (graph-capturable after
+ * conch_reserve_scratch with conch_scaled_gemm_blockwise_workspace_bytes).
+ */
+int conch_scaled_gemm_blockwise(void* c, const void* a, const void* b, const float* scale_a, const float* scale_b,
+                                const void* bias, int64_t m, int64_t n, int64_t k, int64_t lda, int64_t ldb, int64_t ldc,
+                                int64_t sa_stride_m, int64_t sa_stride_kb, int64_t sb_stride_nb, int64_t sb_stride_kb,
+                                int out_dtype, void* stream);
+/* Upper bound of the scratch (per slot) conch_scaled_gemm_blockwise may need for this shape, under any tuning. */
+int64_t conch_scaled_gemm_blockwise_workspace_bytes(int64_t m, int64_t n, int64_t k);
+/* Host-only plan query (no GPU needed, nothing launched): *kernel = 1 tiles / 2 tiles + split-K / 3 decode kernel, *splits = K
+ * slices, for contiguous operands of this shape under the current tuning keys. */
+int conch_debug_blockwise_plan(int64_t m, int64_t n, int64_t k, int* kernel, int* splits);
 
 #ifdef __cplusplus
 }
